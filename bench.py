@@ -30,10 +30,8 @@ import os
 import sys
 import time
 
-# (before the first HIP call: hardware queues for the batches in flight of `value_concurrent*` -- see basq_amd/__init__.py; the
-#  sequential `value` is unaffected)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
+# (the hardware queues are left as the environment sets them: the batches in flight of `value_concurrent*` share them, the
+#  sequential `value` is unaffected -- see basq_amd.configure_hw_queues)
 import torch                                                     # noqa: E402
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -118,7 +116,22 @@ def parse():
     ap.add_argument("--plain", action="store_true", help="for kernel statistics under rocprofv3: the timed loop, the per-seed "
                     "batches and the traced batch only -- no batches in flight, no back-to-back repetition of the round-1 "
                     "launch, no clock sampler (every block-sum launch in the profile then belongs to a batch)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned -- idx and w "
+                    "of recombination(), as DIR/idx.npy and DIR/w.npy in float64 -- for comparing two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(out_dir, idx, w):
+    """The last timed step's result as the caller receives it: ``idx`` (int64 indices into the pool, stored as float64 -- exact
+    below 2**53) and ``w`` (float64 weights), one ``.npy`` file each (2 x 8 x n bytes)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "idx.npy"), idx.detach().cpu().to(torch.float64).numpy())
+    np.save(os.path.join(out_dir, "w.npy"), w.detach().cpu().to(torch.float64).numpy())
 
 
 def self_launch(n_ranks: int) -> int:
@@ -263,6 +276,8 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, idx, w)                  # (outside the timed region, before any other batch runs)
 
     # ---- per-seed latencies (outside the timed region): one synchronised batch per pool seed, median reported ----
     per_seed_ms = []

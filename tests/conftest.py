@@ -10,7 +10,7 @@ if ROOT not in sys.path:
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "reference: needs /root/reference mounted (this container only)")
+    config.addinivalue_line("markers", "reference: bit-for-bit against the reference's own outputs (stored under tests/golden/)")
 
 
 def pytest_collection_modifyitems(config, items):

@@ -7,8 +7,8 @@ Stream A: the 14-class block-sum launch of a headline batch (~6-7 ms).  Stream B
 (1024 threads x 128 VGPRs; 160 KB of LDS) B waits for A's grid to drain; a form whose work-groups fit into the hole ONE
 block-sum work-group leaves (4 waves, <= 204 VGPRs) could run beside it.
 """
-import sys, time, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from basq_amd._ops import HipOps
 from basq_amd._partition import RoundGeometry
 from basq_amd.kernels import StationaryKernel

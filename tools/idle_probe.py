@@ -11,7 +11,7 @@ are NOT slower than back to back -- the penalty belongs to the long, chip-fillin
 the chain (no counter for the shader clock is readable from here; the mechanism is not pinned down).
 """
 import os, sys, time, torch
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from basq_amd._ops import HipOps
 from basq_amd._partition import RoundGeometry
 from basq_amd.kernels import StationaryKernel
