@@ -56,6 +56,18 @@ CASES = [
                                                       warp="wsabil"), pool_seed=15),
     case("wsabim_noise_ragged", 4_321, 4, 70, 25, K("rbf", 2.0, 1.0, posterior=dict(n_obs=50, noise=1e-2, obs_seed=16),
                                                      warp="wsabim"), pool_seed=16),
+    # dimensions above 10: each routes the recombination's block sums through an instantiation no smaller case reaches
+    # (KK = KP/4, KP = 4 ceil((d + 2)/4); XS 2 = stationary exponential, XS 1 = the accurate one of posteriors and WSABI)
+    case("rbf_2e4_d24", 20_000, 24, 200, 100, K("rbf", 3.5), pool_seed=21),                    # KK 7, no kernel weights
+    case("matern52_2e4_d20", 20_000, 20, 200, 100, K("matern52", 3.5), pool_seed=22),          # KK 6, no kernel weights
+    case("matern32_2e4_d38", 20_000, 38, 200, 100, K("matern32", 5.0), pool_seed=23),          # KK 10, prefetch depth 1
+    case("rbf_2e4_d36", 20_000, 36, 200, 100, K("rbf", 4.5), pool_seed=24),                    # KK 10, no kernel weights, depth 1
+    case("posterior_1e4_d16", 10_000, 16, 100, 100, K("rbf", 3.0, 1.2, posterior=dict(n_obs=80, noise=1e-10, obs_seed=25)),
+         pool_seed=25),                                                                        # KK 5, XS 1, two row tiles
+    case("wsabil_1e4_d28", 10_000, 28, 100, 100, K("rbf", 4.0, 1.0, posterior=dict(n_obs=80, noise=1e-10, obs_seed=26),
+                                                   warp="wsabil"), pool_seed=26),             # KK 8, XS 1, kernel weights
+    case("wsabim_8e3_d20", 8_000, 20, 100, 50, K("rbf", 3.0, 1.0, posterior=dict(n_obs=60, noise=1e-3, obs_seed=27),
+                                                 warp="wsabim"), pool_seed=27),               # squared sums at KK 6
     # BASELINE config 2: N=1e5, d=10, n=100, m=1e3.
     case("cfg2_rbf_1e5", 100_000, 10, 1_000, 100, K("rbf", 2.0)),
     # BASELINE config 3 / headline metric: N=1e6, d=10, n=100, m=1e4 (reference: ~2 min of CPU).

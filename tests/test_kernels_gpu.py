@@ -26,7 +26,7 @@ def _rand(n, d, seed):
 
 
 @pytest.mark.parametrize("family", ["rbf", "matern52", "matern32"])
-@pytest.mark.parametrize("d", [1, 2, 3, 7, 10, 14, 32, 38])
+@pytest.mark.parametrize("d", [1, 2, 3, 7, 10, 14, 16, 20, 24, 28, 32, 38])
 def test_gram_vs_oracle(hip_ops, family, d):
     from oracle.kernels_oracle import StationaryOracle
 

@@ -54,6 +54,7 @@ def test_oracle_reproduces_golden(name):
     assert len(tr.rounds) == fx["n_rounds"]
     for mine, ref in zip(tr.rounds, fx["rounds"]):
         assert mine.kept_sets is None or mine.kept_sets.tolist() == ref["kept"]
+    assert tr.tie_margin > 1e-7, f"{name}: a pivot within {tr.tie_margin:.1e} of a tie -- the golden is not a stable yardstick"
 
 
 def test_selection_invariant_under_basis_sign_flips():

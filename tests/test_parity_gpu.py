@@ -260,15 +260,15 @@ def test_structured_differential_fuzz_gpu():
             unstable_log.append(label + f"; reference vs itself: idx moves {ref_idx_moves}, rel {ref_rel:.2e}")
         print("\n".join(unstable_log))
         assert compared >= 100 and min(kinds) >= 20, (compared, kinds)
-        # (review r04: "a regression from 6 to 12 passes silently"; ADVICE r5: an exact set breaks on any legitimate 1-ulp change.)
-        # Every member has shown the reference's own instability above; the KNOWN members are the expected ones, at most two
-        # further cases may cross the bar (another compiler, another exponential) before this is a regression worth a look,
-        # and a known case coming back inside the bar is only reported
+        # (review r04: "a regression from 6 to 12 passes silently"; ADVICE r6: two new members passed with only a warning.)
+        # Every member has shown the reference's own instability above; a case outside the bar that is not in the list fails:
+        # adding a member means editing STRUCTURED_FUZZ_UNSTABLE on purpose.  A known case coming back inside the bar (another
+        # compiler, another exponential: a legitimate 1-ulp change) is only reported.
         new = sorted(set(unstable_cases) - set(STRUCTURED_FUZZ_UNSTABLE))
         back = sorted(set(STRUCTURED_FUZZ_UNSTABLE) - set(unstable_cases))
-        if new or back:
-            warnings.warn(f"structured fuzz: cases outside the bar changed -- new {new}, back inside {back}")
-        assert len(new) <= 2, (unstable_cases, unstable_log)
+        if back:
+            warnings.warn(f"structured fuzz: known cases back inside the bar: {back}")
+        assert not new, f"structured fuzz: cases outside the bar not in STRUCTURED_FUZZ_UNSTABLE: {new}\n" + "\n".join(unstable_log)
     finally:
         torch.set_default_dtype(prev)
 
@@ -387,7 +387,8 @@ def test_index_mismatch_is_attributed_to_the_posterior_cancellation_not_to_the_s
                 runs[key] = ie.cpu().tolist()
             default = runs[(False, True, True)]
             if default == io.tolist():
-                return                                               # (a change made the case match: nothing left to attribute)
+                pytest.fail("structured seed 8 case 33 now selects the reference's indices: nothing is left to attribute -- "
+                            "update this pin and DESIGN.md section 2")
             for key, idx in runs.items():
                 assert idx == default, f"BASIS_SVD, GPU_NULLSPACE, GPU_RANGE_FINDER = {key} changes the engine's selection"
             k = c["kernel"]
@@ -457,7 +458,8 @@ def test_golden_parity_descriptor_driven_rounds(name):
 
 @pytest.mark.parametrize("name", ["rbf_1e4", "rbf_2e4_defaults", "rbf_ragged", "matern52_3e4_d32", "cfg2_rbf_1e5", "cfg3_rbf_1e6",
                                   "cfg4_matern52_1e6_d32", "cfg1_posterior_1e4", "wsabil_2e4", "matern52_posterior",
-                                  "posterior_noise_ragged", "wsabil_noise_ragged", "cfg5_wsabil_5e5"])
+                                  "posterior_noise_ragged", "wsabil_noise_ragged", "cfg5_wsabil_5e5", "rbf_2e4_d24",
+                                  "wsabim_8e3_d20"])
 def test_golden_parity_column_epochs_and_round5_epochs(name):
     """Round 6: inside an epoch the candidates outside the residue classes are message columns (``basq_amd/_epochs.py``; the default
     for these cases) -- against the goldens with EVERY round's kept sets (a trace read after the fact), and against the round-5
